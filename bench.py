@@ -14,6 +14,14 @@ depth-1 partition of the cluster tree (DefaultApproximationBuilder's decompositi
 RCCL all-gather of the x slices followed by the local product (strong scaling: total work fixed).
 value = algorithmic bytes of all ranks / time; the roofline object prices the dominant
 kernel (phase B, tile_gemv_wide) with HIP events recorded on its stream inside the timed region.
+
+--dump-outputs DIR (e.g. bench_outputs/): after the timed steps, what the last of them computed is written as float64
+.npy files, so that two builds can be compared output for output (the inputs depend only on the arguments):
+    y.npy               the product y (shape (rhs, n) with --rhs > 1), user numbering
+    y_rank<r>.npy       with several ranks: rank r's rows of y, cluster numbering
+    x.npy, residuals.npy  with --gmres: the solution of the timed solve (x_rank<r>.npy per rank) and its residual history
+Complex arrays get a trailing axis [real, imag].  Above 64 MB in all, every array keeps the same fixed sample (seed 0)
+of positions along its last axis, listed in <name>_index.npy.
 """
 import argparse
 import json
@@ -26,6 +34,30 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md; measured copy ceiling 6290)
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(directory, arrays, budget):
+    """Writes every array of `arrays` (name -> numpy array) as directory/<name>.npy in float64, complex ones with a trailing
+    axis [real, imag].  When the data exceed `budget` bytes, every array above 1 MB keeps the same fraction of positions
+    along its last axis, drawn with a fixed seed, and the positions kept go to <name>_index.npy (float64, exact)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    nbytes = {k: a.size * (16 if np.iscomplexobj(a) else 8) for k, a in arrays.items()}
+    large = [k for k in arrays if nbytes[k] > 1_000_000]
+    budget -= 4096 * 2 * len(arrays) + sum(nbytes[k] for k in arrays if k not in large)  # (.npy headers, small arrays whole)
+    cost = sum(nbytes[k] + 8 * arrays[k].shape[-1] for k in large)  # (with the index)
+    frac = min(1.0, budget / max(cost, 1))
+    for name, a in arrays.items():
+        if frac < 1.0 and name in large:
+            idx = np.sort(np.random.RandomState(0).choice(a.shape[-1], max(1, int(a.shape[-1] * frac)), replace=False))
+            a = a[..., idx]
+            np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def kernel_source_sha1():
@@ -180,8 +212,8 @@ def main():
                          "multi-rank logic can be rehearsed with several ranks on ONE GPU (not a benchmark)")
     ap.add_argument("--recompress", action="store_true", help="run Htool.recompression (device SVD recompression of the low-rank leaves) after the build")
     ap.add_argument("--rhs", type=int, default=1, help="right-hand sides per step (H @ X, one sweep of the panels per 8 columns); 1 = the headline matvec")
-    ap.add_argument("--gmres", type=int, default=0, help="BASELINE config 5: instead of bare products, a step is ONE GMRES iteration (restart = this value) "
-                                                        "on (shift I + H) with device-resident Krylov vectors")
+    ap.add_argument("--gmres", type=int, default=0, help="BASELINE config 5: instead of bare products, a step is ONE GMRES iteration (restart = this value, "
+                                                        "--steps iterations) on (shift I + H) with device-resident Krylov vectors")
     ap.add_argument("--shift", type=float, default=0.0, help="diagonal shift of the --gmres system (0: N/50, keeps the system well posed)")
     ap.add_argument("--symmetric", choices=["full", "one-triangle"], default=None,
                     help="build with symmetry 'S' / UPLO 'L' (single GPU only): 'full' stores both triangles (the default engine "
@@ -194,7 +226,11 @@ def main():
                                                                   "(code objects, streams, first touch of the memory); default: the operator is built twice and both "
                                                                   "times are reported")
     ap.add_argument("--check", action="store_true", help="(kept for compatibility: the error against sampled exact rows is always reported)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float64, "
+                                                                          "64 MB at most; see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # stdout carries exactly ONE line (the JSON): libraries that chat on stdout (RCCL prints a version banner when a
     # communicator is created) are sent to stderr by pointing fd 1 at fd 2 until the result is ready
     sys.stdout.flush()
@@ -406,12 +442,11 @@ def main():
         x_ref = torch.rand(op.size, dtype=torch.float64, generator=gen_t).to(dtype).cuda()
         b_local = op.apply(x_ref)  # use_ddm_solver.py:60-61: b = A x_ref
         red = op.reduce if dist_mode else None
-        args.steps = args.gmres
 
-        def run_gmres():
-            return gmres(op.apply, b_local, tol=0.0, restart=args.gmres, max_it=args.gmres, reduce=red)
+        def run_gmres(iterations):
+            return gmres(op.apply, b_local, tol=0.0, restart=args.gmres, max_it=iterations, reduce=red)
 
-        run_gmres()  # warm-up cycle (allocations, RCCL channels)
+        run_gmres(args.gmres)  # warm-up cycle (allocations, RCCL channels)
         step = None
     for _ in range(args.warmup if step is not None else 0):
         step()
@@ -421,7 +456,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if step is None:
-        xs_, gmres_info = run_gmres()
+        xs_, gmres_info = run_gmres(args.steps)
         gmres_info["x"] = xs_
     else:
         for _ in range(args.steps):
@@ -431,6 +466,17 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    # steps that ran: a GMRES solve stops early only at an exact breakdown
+    n_timed = args.steps if step is not None else max(1, gmres_info["iterations"])
+    if args.dump_outputs:
+        suffix = f"_rank{rank}" if dist_mode else ""
+        if step is not None:
+            dumped = {"y" + suffix: y.cpu().numpy()}
+        else:
+            dumped = {"x" + suffix: gmres_info["x"].cpu().numpy()}
+            if rank == 0:
+                dumped["residuals"] = np.asarray(gmres_info["residuals"], dtype=np.float64)
+        dump_outputs(args.dump_outputs, dumped, DUMP_LIMIT_BYTES // world)
     n_ph, ph = H.phase_times_us()
     exchange_us = None
     if dist_mode and step is not None:
@@ -494,8 +540,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         dt, tot_bytes, t_build, t_build_cold, t_cluster, t_cluster_cold = float(tmax[0]), float(t[1]), float(tmax[2]), float(tmax[3]), float(tmax[4]), float(tmax[5])
-    ms_per_step = dt / args.steps * 1e3
-    value = tot_bytes / (dt / args.steps) / 1e9
+    ms_per_step = dt / n_timed * 1e3
+    value = tot_bytes / (dt / n_timed) / 1e9
 
     out = {
         "metric": "h_matvec_GBps",
@@ -563,7 +609,7 @@ def main():
                         "true_relative_residual": float(np.sqrt(sq[0] / sq[1])), "solution_error": float(np.sqrt(sq[2] / sq[3])),
                         "shift": shift, "operator_norm_estimate": norm_est,
                         "system": "(shift I + H) x = b with b = (shift I + H) x_ref, shift = 8e-3 |H| (power iterations): unpreconditioned GMRES needs ~40 iterations for 1e-6",
-                        "note": "step = one GMRES iteration (1 product + CGS2 orthogonalisation), restart = number of steps, device-resident Krylov vectors"}
+                        "note": "step = one GMRES iteration (1 product + CGS2 orthogonalisation), --steps iterations, restart = --gmres, device-resident Krylov vectors"}
     if rank == 0:
         t_b = ph[3] * 1e-6 if n_ph else None
         fused = args.symmetric == "one-triangle"

@@ -1,6 +1,6 @@
-"""Generates tests/golden/*.npz.  Run HERE (the build container), where /root/reference exists:
+"""Generates tests/golden/*.npz from a checkout of the reference (htool-python), given as the argument:
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py <path of the reference checkout>
 
 What is pinned: the reference has no golden vectors for the H-matrix path; its tests
 compare against the exact dense operator computed from the generator's kernel.  The only reference
@@ -18,7 +18,9 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.dont_write_bytecode = True  # the reference tree is read-only for this project: no __pycache__ there
-sys.path.insert(0, "/root/reference")
+if len(sys.argv) != 2:
+    sys.exit(__doc__)
+sys.path.insert(0, sys.argv[1])
 from example.create_geometry import create_partitionned_geometries, create_random_geometries  # noqa: E402
 
 

@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,8 +22,10 @@ def _run(cmd):
     return json.loads(lines[0])
 
 
-def test_single_rank_line(built):
-    d = _run([sys.executable, "bench.py", "--points", "60000", "--steps", "4", "--warmup", "2"])
+def test_single_rank_line(built, tmp_path):
+    d = _run([sys.executable, "bench.py", "--points", "60000", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    y = np.load(tmp_path / "y.npy")  # the product of the last timed step, user numbering
+    assert y.dtype == np.float64 and y.shape == (60000,) and np.isfinite(y).all() and np.abs(y).max() > 0
     assert KEYS <= set(d) and d["metric"] == "h_matvec_GBps" and d["unit"] == "GB/s" and d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2
     assert d["higher_is_better"] is True and d["vs_baseline"] is None and d["dtype"] == "f64" and d["data"] == "synthetic" and "workload" in d["config"]
     assert abs(d["value"] - d["algorithmic_GB"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]

@@ -19,6 +19,21 @@ def _timed(fn):
     return time.perf_counter() - t0
 
 
+def _clear_vram(gb=4.0):
+    """The driver clears VRAM on its first use (~27 ms per GB) and what a process frees in the background (~45 ms per GB), and an
+    allocation waits for that (NOTES.md).  The first 16-wide product allocates its ~1 GB workspace: pass `gb` GB through the
+    driver and wait for its wipe, so that the allocation finds cleared memory whatever the box or the earlier tests left."""
+    import torch
+
+    a = torch.empty(int(gb * 1e9), dtype=torch.uint8, device="cuda")
+    a.zero_()
+    torch.cuda.synchronize()
+    del a
+    torch.cuda.empty_cache()
+    torch.cuda.synchronize()
+    time.sleep(1.0 + 0.06 * gb)
+
+
 @pytest.mark.parametrize("sym", ["N", "S", "N+T"])
 def test_first_wide_and_transposed_products_of_a_million_point_operator(built, sym):
     import torch
@@ -43,6 +58,7 @@ def test_first_wide_and_transposed_products_of_a_million_point_operator(built, s
     t1 = _timed(lambda: H.matvec_device(X.data_ptr(), Y.data_ptr(), 0, st))
     t1b = _timed(lambda: H.matvec_device(X.data_ptr(), Y.data_ptr(), 0, st))
     y_one = Y[0].clone()
+    _clear_vram()
     first = _timed(lambda: H.matmat_device(X.data_ptr(), n, Y.data_ptr(), n, 16, 0, st))
     second = _timed(lambda: H.matmat_device(X.data_ptr(), n, Y.data_ptr(), n, 16, 0, st))
     print("sym %s: one column %.1f / %.1f ms; 16 columns first %.1f ms, second %.1f ms" % (sym, 1e3 * t1, 1e3 * t1b, 1e3 * first, 1e3 * second))
